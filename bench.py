@@ -9,9 +9,17 @@ A step = one pass of the hash stage over the device-resident reads:
 pack -> k-mer emit -> (hash, loc) radix sort -> bucket/list build ->
 edge<->middle pair count + collision filter -> candidate ordering
 (KmerTable.calcPairData + calcDispatchData).  `value` = candidate k-mer (role)
-pairs per second summed over ranks.  The end-to-end config (banded HOXD
-dovetail alignment of every dispatched pair) is timed in a second loop and
-reported as aligned_read_pairs_per_s.
+pairs per second summed over ranks.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) only sets up, warms up,
+times the N steps and prints the result line.  `--dump-outputs DIR` also writes
+what the last timed step computed (the dispatch list a caller of the build
+receives, and its statistics) as DIR/<name>.npy.  `--full` adds everything else:
+the instrumented stage loop, the end-to-end config (banded HOXD dovetail
+alignment of every dispatched pair, timed in a second loop and reported as
+aligned_read_pairs_per_s), `--quadratic-steps`, the rooflines, the CPU baselines
+with their CPU/GPU comparisons, the configs[0] / configs[2] FASTA -> .ovl lines
+and `--check-shards`.
 
 Multi-GPU: the sharded context of libsa_overlap
 (include/sa_overlap.h, multi.cpp) -- local k-mer emit, RCCL all-to-all of the
@@ -306,12 +314,49 @@ def note(msg):
 
 T_START = time.perf_counter()
 
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together (well under 64 MB)
+DUMP_STATS = ("kmers", "buckets", "role_pairs", "pairs", "dispatched")  # order of stats.npy
+
+
+def dump_outputs(path, ov, st, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last step --
+    the dispatch list (lead, trail, collision count, in dispatch order; this
+    rank's leads under torchrun) and the build's statistics (DUMP_STATS order) --
+    as <path>/<name><suffix>.npy.  float32 where every value is an integer below
+    2^24 (exact), float64 otherwise.  A dispatch list over the budget is cut to a
+    fixed, seeded sample of its entries: the same positions of all three arrays,
+    in dispatch order, the positions themselves in dispatch_sample_index."""
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        a = np.asarray(a)
+        exact32 = a.size == 0 or (int(a.min()) > -(1 << 24) and int(a.max()) < (1 << 24))
+        np.save(os.path.join(path, name + suffix + ".npy"), a.astype(np.float32 if exact32 else np.float64))
+
+    save("stats", np.array([st[k] for k in DUMP_STATS], dtype=np.uint64))
+    lead, trail, count = ov.dispatch()
+    n = len(lead)
+    keep = DUMP_BUDGET_BYTES // (4 * 8)  # three arrays + the positions, 8 bytes each at most
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))
+        save("dispatch_sample_index", idx)
+        lead, trail, count = lead[idx], trail[idx], count[idx]
+    save("dispatch_lead", lead)
+    save("dispatch_trail", trail)
+    save("dispatch_count", count)
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the instrumented "
+                         "stage loop, the aligner loops, the rooflines, the CPU baselines and their CPU/GPU "
+                         "comparisons, the FASTA -> .ovl lines, --quadratic-steps and --check-shards")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (dispatch list and statistics) as DIR/<name>.npy")
     ap.add_argument("--reads", type=int, default=100_000)
     ap.add_argument("--len", type=int, default=500)
     ap.add_argument("--min-len", type=int, default=None,
@@ -319,11 +364,12 @@ def main():
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--gc", type=float, default=0.50)
     ap.add_argument("--coverage", type=float, default=20.0)
-    ap.add_argument("--align-steps", type=int, default=None)
-    ap.add_argument("--cpu-sample-reads", type=int, default=100_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--align-steps", type=int, default=None, help="--full: timed aligner steps (default: steps / 2)")
+    ap.add_argument("--cpu-sample-reads", type=int, default=100_000, help="--full: reads of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines and the FASTA -> .ovl lines")
     ap.add_argument("--quadratic-steps", type=int, default=0,
-                    help="also time --quadratic-align (full-matrix local alignment) over the same dispatch")
+                    help="--full: also time --quadratic-align (full-matrix local alignment) over the same dispatch")
     ap.add_argument("--align-kernel", type=int, default=0,
                     help="SA_OPT_ALIGN_KERNEL: 0 auto, 1 lane-group (LDS), 2 lane-per-pair")
     ap.add_argument("--replicas", action="store_true", help="torchrun: independent per-rank datasets, no exchange")
@@ -339,12 +385,16 @@ def main():
                     help="sharded: SA_OPT_PASS_BUDGET_MB (partials per shard and lead-range pass; 0 = from "
                          "the free device memory)")
     ap.add_argument("--stage-steps", type=int, default=5,
-                    help="steps of a second, instrumented loop (HIP events around every stage) for the stage "
+                    help="--full: steps of a second, instrumented loop (HIP events around every stage) for the stage "
                          "times and the rooflines; the timed loop itself runs without events")
     ap.add_argument("--check-shards", type=int, default=0,
-                    help="single mode: afterwards rebuild the same reads over S virtual shards and require the "
+                    help="--full, single mode: afterwards rebuild the same reads over S virtual shards and require the "
                          "identical dispatch (a size-independent parity property at full size)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.quadratic_steps > 0 or args.check_shards > 1):
+        ap.error("--quadratic-steps and --check-shards need --full")
 
     ws, rank, local = dist_env()
     if ws > 1 and args.gpus not in (1, ws):
@@ -452,6 +502,56 @@ def main():
     t_build = max_over_ranks(time.perf_counter() - t0)
     st = ov.stats()
     xbytes = (ov.exchanged_bytes() - xb0) / max(args.steps, 1)
+    role_pairs_total = sum_over_ranks(float(st["role_pairs"])) * args.steps
+    value = role_pairs_total / t_build
+    ms_step = t_build / args.steps * 1e3
+    note("hash stage timed: %.3f ms/step" % ms_step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ov, st, "_rank%d" % rank if ws > 1 else "")
+    dhash = None
+    if args.dispatch_hash:
+        ld, tr, ct = (np.asarray(x, dtype=np.uint64) for x in ov.dispatch())
+        w = np.arange(1, len(ld) + 1, dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            dhash = "%016x" % int(np.bitwise_xor.reduce((ld * np.uint64(0x9E3779B97F4A7C15) + tr * np.uint64(
+                0xC2B2AE3D27D4EB4F) + ct * np.uint64(0x165667B19E3779F9)) * w) if len(ld) else 0)
+    # the result line of a plain run; --full adds its fields below
+    line = {
+        "metric": "candidate k-mer pairs/sec (hash stage) + aligned read-pairs/sec, k=15, 500 bp reads",
+        "value": round(value, 1),
+        "unit": "candidate k-mer pairs/s",
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3),
+        "first_build_ms": {"incl_allocation": round(t_first * 1e3, 3),
+                           "second": round(t_second * 1e3, 3) if t_second is not None else None},
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic (splitmix64 genome, error-free reads)",
+        "config": {"workload": workload_label(args.reads, args.len, args.min_len, args.k, n_gpus, mode),
+                   "reads_per_gpu": args.reads, "read_len": args.len, "min_len": args.min_len, "k": args.k,
+                   "genome_bp_per_gpu": G, "ids": "wide", "pmc_key": tag,
+                   "parallelism": {"rank": "rccl-a2a, one process per GPU", "process":
+                                   "rccl-a2a, one process over %d devices" % n_gpus,
+                                   "virtual": "%d virtual shards on one GPU" % args.shards,
+                                   "replicas": "replicas (no exchange)", "single": "single"}[mode]},
+        "per_gpu": {k: int(v) for k, v in st.items() if k not in ("aligned", "ovl_records", "dp_cells")},
+        "exchange_bytes_per_step": int(xbytes) if sharded else None,
+        "shard_info": ov.shard_info() if sharded else None,
+        "dispatch_hash": dhash,
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        ov.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     stage_steps = max(1, args.stage_steps)
     ov.set_timing(True)
     ov.reset_stage_times()
@@ -464,10 +564,7 @@ def main():
     barrier()
     t_instr = max_over_ranks(time.perf_counter() - t0)
     stages = ov.stage_times()
-    role_pairs_total = sum_over_ranks(float(st["role_pairs"])) * args.steps
-    value = role_pairs_total / t_build
 
-    note("hash stage timed: %.3f ms/step" % (t_build / args.steps * 1e3))
     # ---- end-to-end incl. banded HOXD alignment (configs[2]) --------------
     asteps = max(1, args.align_steps) if args.align_steps is not None else max(1, args.steps // 2)  # (>= 1: the aligner fields need one timed step)
     # first align of a sharded context all-gathers the packed reads: timed apart
@@ -524,7 +621,6 @@ def main():
     bases_g = float(offsets[-1])
     step_bytes = bases_g / 4.0 + 32.0 * kmers_g + 16.0 * pairs_g
     rows, pmc_src = pmc_summary(tag)
-    ms_step = t_build / args.steps * 1e3
 
     def roof(bytes_, ms, kernels, name):
         ach = bytes_ / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
@@ -700,13 +796,6 @@ def main():
                                            "file -> .ovl file" % (args.reads, args.len, args.k))
 
     note("aligner timed")
-    dhash = None
-    if args.dispatch_hash:
-        ld, tr, ct = (np.asarray(x, dtype=np.uint64) for x in ov.dispatch())
-        w = np.arange(1, len(ld) + 1, dtype=np.uint64)
-        with np.errstate(over="ignore"):
-            dhash = "%016x" % int(np.bitwise_xor.reduce((ld * np.uint64(0x9E3779B97F4A7C15) + tr * np.uint64(
-                0xC2B2AE3D27D4EB4F) + ct * np.uint64(0x165667B19E3779F9)) * w) if len(ld) else 0)
     # ---- full-size parity property: S virtual shards == one device ----------
     check = None
     if args.check_shards > 1 and mode == "single":
@@ -727,31 +816,9 @@ def main():
             check["error"] = str(e)
 
     if rank == 0:
-        line = {
-            "metric": "candidate k-mer pairs/sec (hash stage) + aligned read-pairs/sec, k=15, 500 bp reads",
-            "value": round(value, 1),
-            "unit": "candidate k-mer pairs/s",
-            "n_gpus": n_gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "first_build_ms": {"incl_allocation": round(t_first * 1e3, 3),
-                               "second": round(t_second * 1e3, 3) if t_second is not None else None},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic (splitmix64 genome, error-free reads)",
-            "config": {"workload": workload_label(args.reads, args.len, args.min_len, args.k, n_gpus, mode),
-                       "reads_per_gpu": args.reads, "read_len": args.len, "min_len": args.min_len, "k": args.k,
-                       "genome_bp_per_gpu": G, "ids": "wide", "pmc_key": tag,
-                       "parallelism": {"rank": "rccl-a2a, one process per GPU", "process":
-                                       "rccl-a2a, one process over %d devices" % n_gpus,
-                                       "virtual": "%d virtual shards on one GPU" % args.shards,
-                                       "replicas": "replicas (no exchange)", "single": "single"}[mode]},
+        line.update({
             "aligned_read_pairs_per_s": round(aligned_total / t_align, 1),
             "ms_per_align_step": round(t_align / asteps * 1e3, 3),
-            "per_gpu": {k: int(v) for k, v in st.items() if k not in ("aligned", "ovl_records", "dp_cells")},
             "dp_cells_per_align_step": int(ast["dp_cells"]),
             "ms_per_step_instrumented": round(t_instr / stage_steps * 1e3, 3),
             "stage_ms_per_step": {k: round(v[0] / stage_steps, 4) for k, v in stages.items() if v[1]},
@@ -761,15 +828,12 @@ def main():
             "roofline_step": roofline_step,
             "roofline_pair_count": roofline_pc,
             "roofline_align": roofline_align,
-            "exchange_bytes_per_step": int(xbytes) if sharded else None,
-            "shard_info": ov.shard_info() if sharded else None,
             "read_allgather_ms": round(t_gather * 1e3, 3) if t_gather is not None else None,
             "cpu_baseline": cpu,
             "config0": config0,
             "config2_end_to_end": config2_e2e,
             "check_shards": check,
-            "dispatch_hash": dhash,
-        }
+        })
         print(json.dumps(line), flush=True)
     ov.close()
     if dist is not None:

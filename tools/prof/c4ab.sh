@@ -1,16 +1,16 @@
 #!/bin/bash
 # configs[4]'s k = 12 per-GPU slice under variant libraries and knobs:
 #   VARIANTS="dir[:ENV=v[,ENV=v]] ..."  (dirs under sequence-aligner_amd/), one bench line each
-# -> gpurun_out/c4ab/<n>.json; summary lines (pairs stage ms, step ms, dispatch hash) in c4ab/ab.txt
+# -> $SA_PROF_OUT/c4ab/<n>.json (default prof_out/c4ab/); summary lines (pairs stage ms, step ms, dispatch hash) in c4ab/ab.txt
 set -u
-O=gpurun_out/c4ab
+O=${SA_PROF_OUT:-prof_out}/c4ab
 mkdir -p $O
 i=0
 for v in $VARIANTS; do
     dir=${v%%:*}; envs=""
     [ "$dir" != "$v" ] && envs=$(echo "${v#*:}" | tr ',' ' ')
     i=$((i+1))
-    env SA_OVERLAP_LIB=$PWD/sequence-aligner_amd/$dir/libsa_overlap.so $envs timeout -k 10 240 python bench.py --no-cpu-baseline \
+    env SA_OVERLAP_LIB=$PWD/sequence-aligner_amd/$dir/libsa_overlap.so $envs timeout -k 10 240 python bench.py --full --no-cpu-baseline \
         --reads 6250000 --len 1000 --min-len 100 --k 12 --steps 1 --warmup 0 --align-steps 0 --dispatch-hash \
         > $O/$i.log 2>&1
     rc=$?

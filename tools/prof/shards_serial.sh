@@ -3,6 +3,7 @@
 # per-shard stage times for DESIGN.md 7 (profiles/<round>/sharded/).
 set -u
 R=$PWD
-mkdir -p $R/gpurun_out
+O=${SA_PROF_OUT:-$R/prof_out}
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/p_sh -o run -- python3 $R/bench.py --shards 8 --serial-shards --steps 3 --warmup 1 --no-cpu-baseline --align-steps 1 > $R/gpurun_out/p_sh.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_sh -o run -- python3 $R/bench.py --full --shards 8 --serial-shards --steps 3 --warmup 1 --no-cpu-baseline --align-steps 1 > $O/p_sh.log 2>&1 || exit 1

@@ -3,26 +3,27 @@
 # counter group (FETCH_SIZE / WRITE_SIZE / SQ), all on the SAME workload, so the
 # summary (tools/pmc_summary.py) is keyed to it.  Usage:
 #   tools/prof/slice_prof.sh <name> <bench args...>
-# Outputs under gpurun_out/sp_<name>/; stops at the first failure.
+# Outputs under $SA_PROF_OUT/sp_<name>/ (default prof_out/sp_<name>/); stops at the first failure.
 set -u
 R=$GRAFT_REPO_ROOT
+O=${SA_PROF_OUT:-$R/prof_out}
 NAME=$1; shift
-OUT=$R/gpurun_out/sp_$NAME
+OUT=$O/sp_$NAME
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="$R/bench.py --no-cpu-baseline $*"
+BENCH="$R/bench.py --full --no-cpu-baseline $*"
 timeout -k 10 400 python3 $BENCH > $OUT/bench.log 2>&1
-rc=$?; echo "sp_$NAME bench rc=$rc" >> $R/gpurun_out/steps.txt
+rc=$?; echo "sp_$NAME bench rc=$rc" >> $O/steps.txt
 [ $rc -eq 0 ] || exit $rc
 tail -1 $OUT/bench.log > $OUT/bench.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 $BENCH > $OUT/prof.log 2>&1
-rc=$?; echo "sp_$NAME prof rc=$rc" >> $R/gpurun_out/steps.txt
+rc=$?; echo "sp_$NAME prof rc=$rc" >> $O/steps.txt
 [ $rc -eq 0 ] || exit $rc
 pass() {  # pass <name> <counters...>
     local p=$1; shift
     timeout -k 10 400 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$p -o pmc -- python3 $BENCH > $OUT/pmc_$p.log 2>&1
     local rc=$?
-    echo "sp_$NAME pmc_$p rc=$rc" >> $R/gpurun_out/steps.txt
+    echo "sp_$NAME pmc_$p rc=$rc" >> $O/steps.txt
     [ $rc -eq 0 ] || exit $rc
 }
 pass fetch FETCH_SIZE
@@ -36,5 +37,5 @@ python3 $R/tools/pmc_summary.py $OUT $OUT/pmc_summary__$KEY.csv
 # traces pass gpurun's 64 MiB copy-back limit)
 if [ -n "${SP_TRIM:-}" ]; then
     rm -f $OUT/pmc_*/pmc_kernel_trace.csv $OUT/pmc_*/pmc_counter_collection.csv $OUT/prof/run_kernel_trace.csv
-    du -sh $OUT >> $R/gpurun_out/steps.txt
+    du -sh $OUT >> $O/steps.txt
 fi
