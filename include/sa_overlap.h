@@ -79,6 +79,10 @@ typedef struct sa_alignment {
 #define SA_ALN_DUD 1        /* phase-1 backtrack missed j==0 -> BioLibs.dud (BioLibs.scala:694-695) */
 #define SA_ALN_VALID 2      /* Alignment.valid (ObjectStore.scala:102-107) */
 #define SA_ALN_OVL_VALID 4  /* Overlap.valid (ObjectStore.scala:137-141) -> written to the .ovl */
+/* both strands (SA_OPT_STRANDS): the pair was aligned with its trail / its lead
+ * reverse-complemented; lead and trail stay original ids */
+#define SA_ALN_FLIP_TRAIL 8
+#define SA_ALN_FLIP_LEAD 16
 
 typedef struct sa_ctx sa_ctx;
 
@@ -112,6 +116,9 @@ int sa_build_candidates(sa_ctx *ctx);
  * (lead, trail) with its collision count. */
 int sa_get_dispatch(sa_ctx *ctx, const int32_t **lead, const int32_t **trail,
                     const int32_t **count, size_t *n);
+/* One strand code per entry of sa_get_dispatch: 0 forward pair, 1 trail flipped,
+ * 2 lead flipped (SA_OPT_STRANDS); all 0 with the option off. */
+int sa_get_dispatch_strands(sa_ctx *ctx, const uint8_t **strand, size_t *n);
 /* PairData (every counted ordered pair, not only dispatched ones), in the
  * reference's iteration order (STRICT) or by (fst, snd) ascending (WIDE).
  * Requires sa_set_option(ctx, SA_OPT_KEEP_PAIRS, 1) before sa_build_candidates. */
@@ -184,13 +191,57 @@ enum sa_option {
                                   (rho = 1.5 x the partials / bound ratio of these reads,
                                   probed on their first build; one pass whenever the
                                   bound is far from the memory) */
-    SA_OPT_LEAN_MEMORY = 10    /* virtual shards (one device): the shards' transients (sort
+    SA_OPT_LEAN_MEMORY = 10,   /* virtual shards (one device): the shards' transients (sort
                                   and bucket-build scratch, pair-counter regions, reduce
                                   scratch) come from one pool that each shard borrows for
                                   the length of a call, instead of P copies, so that
                                   virtual shards of a large read set fit one device; the
                                   shards then run one after another */
+    SA_OPT_STRANDS = 11        /* enum sa_strands (default SA_STRANDS_FORWARD); changing it
+                                  invalidates the candidates and alignments */
 };
+
+/* Which strands overlaps are searched on.  The reference treats every read as
+ * forward-strand text (Overlap.adj is the constant 'N', ObjectStore.scala:121)
+ * and has no reverse-complement code: SA_STRANDS_BOTH has no reference
+ * counterpart and is defined through the reference's own semantics instead.
+ *
+ * rc(s): s reversed with A<->T and C<->G, every other byte unchanged.  The
+ * augmented set is reads 1..2N with read N + i = rc(read i); D* is
+ * calcPairData + calcDispatchData (KmerTable.scala:85-187) over it with wide
+ * ids, in the canonical wide order (lead descending, trail ascending).  With
+ * SA_STRANDS_BOTH the dispatch, the alignments and the .ovl are
+ *   1. the forward block: exactly the option-off result (same id mode, order, bytes);
+ *   2. the flipped block: the entries (a, b) of D*, in D*'s order, that are
+ *      lead flipped  (strand code 2): a > N >= b and a - N < b, lead = a - N, trail = b, or
+ *      trail flipped (strand code 1): a <= N < b and a < b - N, lead = a, trail = b - N.
+ *      (All lead-flipped entries precede the trail-flipped ones.)  Dropped before
+ *      alignment: rc x rc pairs (the forward block's mirror), the mirror duplicate of
+ *      each flipped pair (the one with the larger original id on the A side), and a
+ *      read against its own reverse complement.
+ * A flipped entry is aligned as the oriented pair (augmented read a, augmented
+ * read b): start / end / correct / error and the DUD / VALID / OVL_VALID flags are
+ * that alignment's, coordinates in the oriented sequences, plus SA_ALN_FLIP_TRAIL
+ * or SA_ALN_FLIP_LEAD.  With (ahg', bhg') the oriented pair's Overlap hangs:
+ * trail flipped ahg = ahg', bhg = bhg'; lead flipped ahg = -bhg', bhg = -ahg' (the
+ * same layout seen with the lead forward and the trail reversed, the reversed read
+ * starting first).  Its .ovl record is today's with adj:I and these hangs -- the
+ * N / I-with-signed-hangs convention of AMOS's own overlappers, parity unpinned
+ * (the reference never emits it).  Alignment errors are the
+ * augmented definition's: a flipped pair that touches a non-ACGT base fails the
+ * call with SA_E_NON_ACGT as a forward one does.
+ *
+ * sa_get_dispatch returns forward block then flipped block with original ids and
+ * collision counts; sa_get_read keeps serving ids 1..N.  sa_stats: dispatched,
+ * aligned, ovl_records and dp_cells count both blocks; kmers, buckets, role_pairs,
+ * pairs and flags describe the augmented table (kmers is twice the forward value).
+ * The reverse-complement kernel is timed under SA_STAGE_PACK, the strand filter
+ * under SA_STAGE_ORDER.
+ *
+ * SA_E_ARG on a sharded, rank or sa_dist_* context, and together with
+ * SA_ALIGNER_QUADRATIC or SA_OPT_KEEP_PAIRS (whichever option is set second is
+ * refused): those combinations are follow-ups. */
+enum sa_strands { SA_STRANDS_FORWARD = 0, SA_STRANDS_BOTH = 1 };
 
 /* Project4's fdAlign switch (Project4.scala:187-192, :585-604).
  * LINEAR     --linear-align (default): generateFastDovetailAlignmentSet, banded

@@ -281,7 +281,10 @@ int upload_reads(sa_ctx *c) {
     const uint32_t n = (uint32_t)(c->boff.size() - 1);
     uint8_t *ascii; uint64_t *boff, *woff, *occ; int32_t *len; uint32_t *codes; int32_t *bad;
     uint32_t *lbase, *lrank; uint8_t *tag;
-    ENSURE(c->d_ascii, c->bases.size() + 32, &ascii);  // pack_reads reads 20 bytes past a word start
+    // pack_reads reads 20 bytes past a word start; both strands: the reverse complements
+    // follow the reads (revcomp_kernel), the padding after them.  (The child context of
+    // a both-strand build holds no bases: its buffer is the parent's.)
+    ENSURE(c->d_ascii, c->bases.size() * (c->strands == SA_STRANDS_BOTH ? 2 : 1) + 32, &ascii);
     ENSURE(c->d_boff, n + 1, &boff);
     ENSURE(c->d_woff, n + 1, &woff);
     ENSURE(c->d_len, n + 1, &len);
@@ -1667,6 +1670,9 @@ static inline char *put_int(char *p, int32_t v) {
     return p;
 }
 
+int strand_fetch(sa_ctx *a);
+int strand_append_results(sa_ctx *c);
+
 int host_results(sa_ctx *c) {
     if (c->host_valid) return SA_OK;
     const uint64_t nd = c->n_disp;
@@ -1674,13 +1680,36 @@ int host_results(sa_ctx *c) {
         HostScope hs(c, SA_STAGE_READBACK);
         c->alns.resize(nd);
         if (nd) HIPCHK(hipMemcpy(c->alns.data(), c->d_aln.p, nd * sizeof(sa_alignment), hipMemcpyDeviceToHost));
+        if (c->aug_of) {
+            // the flipped block: the oriented pairs' alignments under their original ids; a
+            // lead-flipped pair's hangs are the same layout seen with the lead forward and
+            // the trail reversed (ahg = -bhg', bhg = -ahg'; |ahg|, |bhg| and so
+            // Overlap.valid unchanged)
+            int rc = strand_fetch(c);
+            if (rc) return rc;
+            for (uint64_t i = 0; i < nd; ++i) {
+                sa_alignment &a = c->alns[i];
+                a.lead = c->s_lead[i];
+                a.trail = c->s_trail[i];
+                if (c->s_code[i] == 2) {
+                    const int32_t t = a.ahg;
+                    a.ahg = -a.bhg;
+                    a.bhg = -t;
+                    a.flags |= SA_ALN_FLIP_LEAD;
+                } else
+                    a.flags |= SA_ALN_FLIP_TRAIL;
+            }
+        }
     }
     HostScope hs(c, SA_STAGE_FORMAT);
     // "{OVL\nadj:N\nrds:" + lead + "," + trail + "\nscr:0\nahg:" + ahg + "\nbhg:" + bhg + "\n}" + "\n"
     // (Overlap.print, ObjectStore.scala:127-135; Project4.scala:814-818).  In chunks on up to 8
     // host threads: each chunk's exact byte count first, then every chunk formats straight into
     // its place (round 6: 7 ms for configs[0]'s 366k records on one thread)
-    static const char H1[] = "{OVL\nadj:N\nrds:", H2[] = "\nscr:0\nahg:", H3[] = "\nbhg:", H4[] = "\n}\n";
+    // (adj:I for the flipped block of a both-strand run, with the hangs above)
+    char H1[] = "{OVL\nadj:N\nrds:";
+    if (c->aug_of) H1[9] = 'I';
+    static const char H2[] = "\nscr:0\nahg:", H3[] = "\nbhg:", H4[] = "\n}\n";
     constexpr size_t FIXED = (sizeof(H1) - 1) + 1 + (sizeof(H2) - 1) + (sizeof(H3) - 1) + (sizeof(H4) - 1);
     auto ndig = [](int32_t v) {
         uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
@@ -1741,7 +1770,157 @@ int host_results(sa_ctx *c) {
         }
     });
     c->stats.ovl_records = rec;
+    if (c->strands == SA_STRANDS_BOTH) {
+        int rc = strand_append_results(c);
+        if (rc) return rc;
+    }
     c->host_valid = true;
+    return SA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// both strands (SA_OPT_STRANDS = SA_STRANDS_BOTH, include/sa_overlap.h)
+// ---------------------------------------------------------------------------
+int child_fail(sa_ctx *c, int rc) { return fail(c, rc, c->aug ? c->aug->err : std::string("both strands")); }
+
+// the child context of the augmented set, its options and read offsets brought up to date
+int strand_sync_child(sa_ctx *c) {
+    const uint64_t n = c->boff.size() - 1;
+    if (2 * n > 0x7FFFFFF0ull) return fail(c, SA_E_OVERFLOW, "both strands: more than 2^30 reads");
+    if (!c->aug) {
+        sa_ctx *a = new sa_ctx();
+        a->device = c->device;
+        if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
+            delete a;
+            return fail(c, SA_E_HIP, "both strands: hipStreamCreateWithFlags failed");
+        }
+        a->aug_of = c;
+        c->aug = a;
+        c->aug_gen = ~0ull;
+    }
+    sa_ctx *a = c->aug;
+    a->set = c->set;
+    a->set.id_mode = SA_IDS_WIDE;
+    a->timing = c->timing;
+    a->align_kernel = c->align_kernel;
+    a->first_pass = c->first_pass;
+    a->launch_slice = c->launch_slice;
+    if (c->aug_gen != c->reads_gen) {
+        // host metadata of the 2N reads from the lengths alone: read N + i has read i's length
+        const uint64_t total = c->boff[n];
+        a->boff.resize(2 * n + 1);
+        for (uint64_t i = 0; i <= n; ++i) a->boff[i] = c->boff[i];
+        for (uint64_t i = 1; i <= n; ++i) a->boff[n + i] = total + (c->boff[i] - c->boff[0]);
+        a->reads_dirty = true;
+        a->built = a->aligned = false;
+        ++a->reads_gen;
+        c->aug_gen = c->reads_gen;
+    }
+    a->d_ascii.p = c->d_ascii.p;
+    a->d_ascii.bytes = c->d_ascii.bytes;
+    a->d_ascii.borrowed = true;
+    return SA_OK;
+}
+
+// after the forward build: the augmented set's build and the strand filter
+int strand_build(sa_ctx *c, bool readback) {
+    c->built = false;  // (until the flipped block stands)
+    c->b_valid = false;
+    if (c->boff[0] != 0) return fail(c, SA_E_ARG, "both strands: read offsets must start at 0");
+    int rc = strand_sync_child(c);
+    if (rc) return rc;
+    sa_ctx *a = c->aug;
+    const uint32_t n = (uint32_t)(c->boff.size() - 1);
+    if ((rc = ensure_prepared(a))) return child_fail(c, rc);
+    {
+        StageScope st(a, SA_STAGE_PACK);
+        HIPCHK(launch_revcomp((uint8_t *)a->d_ascii.p, (const uint64_t *)a->d_boff.p, n, a->stream));
+    }
+    if ((rc = device_build(a, false))) return child_fail(c, rc);
+    a->built = false;
+    a->s_valid = false;
+    const uint64_t nd = a->n_disp;
+    int32_t *ol, *ot, *oc, *al, *at;
+    uint8_t *code;
+    uint32_t *tile;
+    const uint32_t tiles = strand_filter_tiles(nd);
+    ENSURE(a->d_slead, nd, &ol);
+    ENSURE(a->d_strail, nd, &ot);
+    ENSURE(a->d_scount, nd, &oc);
+    ENSURE(a->d_scode, nd, &code);
+    ENSURE(a->d_salead, nd, &al);
+    ENSURE(a->d_satrail, nd, &at);
+    ENSURE(a->d_stile, (size_t)tiles + 2 + scan_temp_bytes(tiles) / 4 + 1, &tile);
+    uint32_t *total = tile + tiles + 1;
+    {
+        StageScope st(a, SA_STAGE_ORDER);
+        HIPCHK(launch_strand_filter((const int32_t *)a->d_lead.p, (const int32_t *)a->d_trail.p,
+                                    (const int32_t *)a->d_count.p, nd, n, tile, total + 1, total, ol, ot, oc, code, al,
+                                    at, a->stream));
+    }
+    uint32_t kept = 0;
+    HIPCHK(hipMemcpyAsync(&kept, total, 4, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    resolve_timing(a);
+    // the aligner takes the context's dispatch arrays: now the kept augmented ids
+    std::swap(a->d_lead, a->d_salead);
+    std::swap(a->d_trail, a->d_satrail);
+    a->n_disp = kept;
+    a->stats.dispatched = kept;
+    a->built = true;
+    if (readback && (rc = strand_fetch(a))) return child_fail(c, rc);
+    c->stats.kmers = a->stats.kmers;
+    c->stats.buckets = a->stats.buckets;
+    c->stats.role_pairs = a->stats.role_pairs;
+    c->stats.pairs = a->stats.pairs;
+    c->stats.flags = a->stats.flags;
+    c->stats.dispatched = c->n_disp + kept;
+    c->built = true;
+    return SA_OK;
+}
+
+// (child) the flipped block's original ids, counts and strand codes on the host
+int strand_fetch(sa_ctx *c) {
+    if (c->s_valid) return SA_OK;
+    const uint64_t nd = c->n_disp;
+    HostScope hs(c, SA_STAGE_READBACK);
+    c->s_lead.resize(nd); c->s_trail.resize(nd); c->s_count.resize(nd); c->s_code.resize(nd);
+    if (nd) {
+        HIPCHK(hipMemcpy(c->s_lead.data(), c->d_slead.p, nd * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->s_trail.data(), c->d_strail.p, nd * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->s_count.data(), c->d_scount.p, nd * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(c->s_code.data(), c->d_scode.p, nd, hipMemcpyDeviceToHost));
+    }
+    c->s_valid = true;
+    return SA_OK;
+}
+
+int strand_align(sa_ctx *c, bool readback) {
+    if (!c->built || !c->aug) return fail(c, SA_E_STATE, "sa_align before sa_build_candidates");
+    int rc = device_align(c, false);
+    if (rc) return rc;
+    sa_ctx *a = c->aug;
+    a->timing = c->timing;
+    a->align_kernel = c->align_kernel;
+    if ((rc = device_align(a, false))) {
+        c->aligned = false;
+        return child_fail(c, rc);
+    }
+    c->stats.aligned += a->stats.aligned;
+    c->stats.dp_cells += a->stats.dp_cells;
+    if (readback) return host_results(c);
+    return SA_OK;
+}
+
+// (parent, after its own records) the flipped block's alignments and adj:I records appended
+int strand_append_results(sa_ctx *c) {
+    sa_ctx *a = c->aug;
+    if (!a || !a->aligned) return fail(c, SA_E_STATE, "both strands: flipped block not aligned");
+    const int rc = host_results(a);
+    if (rc) return child_fail(c, rc);
+    c->alns.insert(c->alns.end(), a->alns.begin(), a->alns.end());
+    c->ovl += a->ovl;
+    c->stats.ovl_records += a->stats.ovl_records;
     return SA_OK;
 }
 
@@ -1749,11 +1928,14 @@ int host_results(sa_ctx *c) {
 
 int single_build(sa_ctx *c, bool readback) {
     (void)hipSetDevice(c->device);
-    return device_build(c, readback);
+    const int rc = device_build(c, readback);
+    if (rc || c->strands != SA_STRANDS_BOTH) return rc;
+    return strand_build(c, readback);
 }
 
 int single_align(sa_ctx *c, bool readback) {
     (void)hipSetDevice(c->device);
+    if (c->strands == SA_STRANDS_BOTH) return strand_align(c, readback);
     return device_align(c, readback);
 }
 
@@ -1804,6 +1986,7 @@ int sa_ctx_create(const sa_settings *s, int device, sa_ctx **out) {
 void sa_ctx_destroy(sa_ctx *c) {
     if (!c) return;
     if (c->multi) multi_destroy(c);
+    if (c->aug) sa_ctx_destroy(c->aug);  // (its ASCII buffer is this context's: borrowed, not freed)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     DBuf *bufs[] = {&c->d_ascii, &c->d_boff, &c->d_woff, &c->d_len, &c->d_codes, &c->d_bad, &c->d_occ_off,
@@ -1818,7 +2001,8 @@ void sa_ctx_destroy(sa_ctx *c) {
                     &c->d_hidx, &c->d_hpos, &c->d_htmp, &c->d_hist, &c->d_hovf, &c->d_hsmall,
                     &c->d_ltb, &c->d_lmax, &c->d_rreg, &c->d_rcnt, &c->d_rex,
                     &c->d_shl, &c->d_sht, &c->d_shc, &c->d_rsh, &c->d_pbound, &c->d_pbown, &c->d_trove, &c->d_prange,
-                    &c->d_pioff, &c->d_pitems};
+                    &c->d_pioff, &c->d_pitems, &c->d_slead, &c->d_strail, &c->d_scount, &c->d_scode, &c->d_salead,
+                    &c->d_satrail, &c->d_stile};
     for (DBuf *b : bufs)
         if (b->p && !b->borrowed) (void)hipFree(b->p);
     for (auto &p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1905,10 +2089,38 @@ int sa_get_dispatch(sa_ctx *c, const int32_t **lead, const int32_t **trail, cons
             HIPCHK(hipMemcpy(c->count.data(), c->d_count.p, c->n_disp * 4, hipMemcpyDeviceToHost));
         }
     }
+    if (c->strands == SA_STRANDS_BOTH && c->aug) {  // forward block, then flipped block
+        sa_ctx *a = c->aug;
+        if (!c->b_valid) {
+            const int rc = strand_fetch(a);
+            if (rc) return child_fail(c, rc);
+            c->b_lead = c->lead; c->b_trail = c->trail; c->b_count = c->count;
+            c->b_lead.insert(c->b_lead.end(), a->s_lead.begin(), a->s_lead.end());
+            c->b_trail.insert(c->b_trail.end(), a->s_trail.begin(), a->s_trail.end());
+            c->b_count.insert(c->b_count.end(), a->s_count.begin(), a->s_count.end());
+            c->b_code.assign(c->lead.size(), 0);
+            c->b_code.insert(c->b_code.end(), a->s_code.begin(), a->s_code.end());
+            c->b_valid = true;
+        }
+        if (lead) *lead = c->b_lead.data();
+        if (trail) *trail = c->b_trail.data();
+        if (count) *count = c->b_count.data();
+        *n = c->b_lead.size();
+        return SA_OK;
+    }
     if (lead) *lead = c->lead.data();
     if (trail) *trail = c->trail.data();
     if (count) *count = c->count.data();
     *n = c->n_disp;
+    return SA_OK;
+}
+
+int sa_get_dispatch_strands(sa_ctx *c, const uint8_t **strand, size_t *n) {
+    if (!c || !strand || !n) return SA_E_ARG;
+    const int rc = sa_get_dispatch(c, nullptr, nullptr, nullptr, n);
+    if (rc) return rc;
+    if (c->strands != SA_STRANDS_BOTH) c->b_code.assign(*n, 0);
+    *strand = c->b_code.data();
     return SA_OK;
 }
 
@@ -2085,7 +2297,27 @@ int sa_write_afg(sa_ctx *c, const char *path, const char *const *eids, int quali
 int sa_set_option(sa_ctx *c, int option, int64_t value) {
     if (!c) return SA_E_ARG;
     switch (option) {
-    case SA_OPT_KEEP_PAIRS: c->keep_pairs = value != 0; break;
+    case SA_OPT_KEEP_PAIRS:
+        if (value != 0 && c->strands == SA_STRANDS_BOTH)
+            return fail(c, SA_E_ARG, "SA_OPT_KEEP_PAIRS with both strands is not supported");
+        c->keep_pairs = value != 0;
+        break;
+    case SA_OPT_STRANDS:
+        if (value != SA_STRANDS_FORWARD && value != SA_STRANDS_BOTH)
+            return fail(c, SA_E_ARG, "SA_OPT_STRANDS must be SA_STRANDS_FORWARD or SA_STRANDS_BOTH");
+        if (value == SA_STRANDS_BOTH) {
+            if (c->multi || c->dist)
+                return fail(c, SA_E_ARG, "both strands on a sharded, rank or sa_dist_* context is not supported");
+            if (c->aligner == SA_ALIGNER_QUADRATIC)
+                return fail(c, SA_E_ARG, "both strands with SA_ALIGNER_QUADRATIC is not supported");
+            if (c->keep_pairs) return fail(c, SA_E_ARG, "both strands with SA_OPT_KEEP_PAIRS is not supported");
+        }
+        if (c->strands != (int)value) {
+            c->strands = (int)value;
+            c->built = c->aligned = false;
+            c->uploaded = false;  // (the ASCII buffer holds one or two halves)
+        }
+        return SA_OK;
     case SA_OPT_TIMING: c->timing = value != 0; break;
     case SA_OPT_ALIGN_KERNEL:
         if (value < 0 || value > 3) return fail(c, SA_E_ARG, "SA_OPT_ALIGN_KERNEL must be 0..3");
@@ -2094,6 +2326,8 @@ int sa_set_option(sa_ctx *c, int option, int64_t value) {
     case SA_OPT_ALIGNER:
         if (value != SA_ALIGNER_LINEAR && value != SA_ALIGNER_QUADRATIC)
             return fail(c, SA_E_ARG, "SA_OPT_ALIGNER must be SA_ALIGNER_LINEAR or SA_ALIGNER_QUADRATIC");
+        if (value == SA_ALIGNER_QUADRATIC && c->strands == SA_STRANDS_BOTH)
+            return fail(c, SA_E_ARG, "SA_ALIGNER_QUADRATIC with both strands is not supported");
         c->aligner = (int)value;
         c->aligned = false;
         break;
@@ -2131,6 +2365,8 @@ int sa_get_stage_times(const sa_ctx *c, double *ms, uint64_t *launches, int n) {
     double m[SA_NUM_STAGES];
     uint64_t k[SA_NUM_STAGES];
     for (int i = 0; i < SA_NUM_STAGES; ++i) { m[i] = c->stage_ms[i]; k[i] = c->stage_n[i]; }
+    if (c->aug)  // both strands: the augmented set's stages
+        for (int i = 0; i < SA_NUM_STAGES; ++i) { m[i] += c->aug->stage_ms[i]; k[i] += c->aug->stage_n[i]; }
     if (c->multi) multi_stage_times(c, m, k);
     for (int i = 0; i < n && i < SA_NUM_STAGES; ++i) {
         if (ms) ms[i] = m[i];
@@ -2142,6 +2378,7 @@ int sa_get_stage_times(const sa_ctx *c, double *ms, uint64_t *launches, int n) {
 int sa_reset_stage_times(sa_ctx *c) {
     if (!c) return SA_E_ARG;
     for (int i = 0; i < SA_NUM_STAGES; ++i) { c->stage_ms[i] = 0; c->stage_n[i] = 0; }
+    if (c->aug) sa_reset_stage_times(c->aug);
     if (c->multi) multi_reset_stage_times(c);
     return SA_OK;
 }
@@ -2150,6 +2387,7 @@ int sa_sync(sa_ctx *c) {
     if (!c) return SA_E_ARG;
     (void)hipSetDevice(c->device);
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->aug) HIPCHK(hipStreamSynchronize(c->aug->stream));
     return c->multi ? multi_sync(c) : SA_OK;
 }
 
@@ -2161,6 +2399,7 @@ uint64_t sa_exchanged_bytes(const sa_ctx *c) { return c ? multi_exchanged_bytes(
 int sa_dist_init(sa_ctx *c, int rank, int nranks, const uint32_t *starts, const int32_t *lengths) {
     if (!c || !starts || !lengths) return SA_E_ARG;
     if (c->multi) return fail(c, SA_E_STATE, "a sharded context exchanges internally (sa_dist_* are per-shard calls)");
+    if (c->strands == SA_STRANDS_BOTH) return fail(c, SA_E_ARG, "both strands on a sa_dist_* context is not supported");
     if (nranks < 1 || nranks > 256 || (nranks & (nranks - 1)) || rank < 0 || rank >= nranks)
         return fail(c, SA_E_ARG, "nranks must be a power of two <= 256 and 0 <= rank < nranks");
     if (c->set.id_mode == SA_IDS_STRICT) return fail(c, SA_E_ARG, "the sharded path runs in wide-id mode only");

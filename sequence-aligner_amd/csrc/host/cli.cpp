@@ -343,6 +343,7 @@ int main(int argc, char **argv) {
     int device = 0;
     bool stats = false;
     int aligner = SA_ALIGNER_LINEAR;
+    int strands = SA_STRANDS_FORWARD;
     std::string action = "calc-overlaps";
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -410,6 +411,8 @@ int main(int argc, char **argv) {
             }
             (a == "--gpus" ? g_gpus : g_shards) = iv;
         }
+        else if (a == "--both-strands") strands = SA_STRANDS_BOTH;      // SA_OPT_STRANDS (no reference counterpart)
+        else if (a == "--forward-strand") strands = SA_STRANDS_FORWARD;  // the default, as the reference
         else if (a == "--stats") stats = true;
         else if (a == "--afg") afg = str();
         else if (a == "--afg-header-eids") afg_header_eids = true;
@@ -433,6 +436,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "No input file specified\n");
         return 255;  // System.exit(-1)
     }
+    if (strands == SA_STRANDS_BOTH && (g_gpus > 1 || g_shards > 1 || aligner == SA_ALIGNER_QUADRATIC)) {
+        fprintf(stderr, "--both-strands cannot be combined with --gpus / --shards above 1 or --quadratic-align\n");
+        return 1;
+    }
     if (action == "test-fasta-read") return mode_test_fasta_read(s, device, input);
     if (action == "bench-fasta-read") return mode_bench_fasta_read(s, device, input);
     if (action == "test-kmer-cover") return mode_test_kmer_cover(s, device, input);
@@ -454,6 +461,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     rc = sa_set_option(ctx, SA_OPT_ALIGNER, aligner);
+    if (rc == SA_OK) rc = sa_set_option(ctx, SA_OPT_STRANDS, strands);
     if (rc == SA_OK && (rc = sa_read_fasta(ctx, input.c_str())) == SA_OK && (rc = sa_build_candidates(ctx)) == SA_OK &&
         (rc = sa_align(ctx)) == SA_OK) {
         rc = sa_write_ovl(ctx, output.empty() ? nullptr : output.c_str());

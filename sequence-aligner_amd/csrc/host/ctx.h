@@ -164,6 +164,22 @@ struct sa_ctx {
     int aligner = SA_ALIGNER_LINEAR;  // SA_OPT_ALIGNER (--linear-align / --quadratic-align)
     uint64_t local_batch_bytes = 16ull << 30;  // traceback-code budget of one quadratic launch
     bool built = false, aligned = false;
+    // both strands (SA_OPT_STRANDS = SA_STRANDS_BOTH): the augmented set, reads 1..2N with
+    // read N + i = rc(read i), lives in a child context `aug` (wide ids; host metadata
+    // from the lengths alone, its ASCII buffer this context's, second half filled by
+    // revcomp_kernel).  The forward block is this context's own build; the flipped block
+    // is aug's dispatch after strand_filter, aligned by aug over the augmented ids
+    int strands = SA_STRANDS_FORWARD;
+    sa_ctx *aug = nullptr;
+    sa_ctx *aug_of = nullptr;        // set on the child: its parent
+    uint64_t aug_gen = ~0ull;        // the parent's reads_gen the child's offsets were made from
+    DBuf d_slead, d_strail, d_scount, d_scode, d_salead, d_satrail, d_stile;  // (child) strand_filter outputs
+    std::vector<int32_t> s_lead, s_trail, s_count;   // (child) flipped block, original ids
+    std::vector<uint8_t> s_code;                     // (child) its strand codes
+    bool s_valid = false;                            // (child) s_* hold this build's flipped block
+    bool b_valid = false;                            // (parent) b_* hold this build's dispatch
+    std::vector<int32_t> b_lead, b_trail, b_count;   // (parent) forward + flipped block (sa_get_dispatch)
+    std::vector<uint8_t> b_code;                     // (parent) strand code per entry (sa_get_dispatch_strands)
 #ifdef SA_PB_STAMPS
     uint64_t *stamps_dev = nullptr;  // (timing probe builds, partition.hip PB_STAMP)
     uint32_t stamps_np = 0;

@@ -411,6 +411,20 @@ hipError_t launch_trove_pair_keys(const int32_t *f, const int32_t *s, uint32_t n
 hipError_t launch_trove_gather3(const uint32_t *order, uint32_t n, const int32_t *f, const int32_t *s, const int32_t *k,
                                 int32_t *fo, int32_t *so, int32_t *ko, hipStream_t st);
 
+// ---- both strands (strand.hip) ------------------------------------------
+// reads 0 .. n-1 of `ascii` (byte offsets boff[0 .. n]) reverse-complemented into
+// [boff[n] + boff[r], boff[n] + boff[r + 1]): the second half of the augmented buffer
+hipError_t launch_revcomp(uint8_t *ascii, const uint64_t *boff, uint32_t n, hipStream_t s);
+// stable compaction of the augmented dispatch (ids 1-based, n_forward = N) into the
+// flipped block: original ids, counts, strand codes (1 trail flipped, 2 lead flipped)
+// and the augmented ids for the aligner; tile_cnt: strand_filter_tiles(n) + 1 u32,
+// scan_tmp: scan_temp_bytes(strand_filter_tiles(n)); the kept total in *total_dev
+uint32_t strand_filter_tiles(uint64_t n);
+hipError_t launch_strand_filter(const int32_t *lead, const int32_t *trail, const int32_t *count, uint64_t n,
+                                uint32_t n_forward, uint32_t *tile_cnt, void *scan_tmp, uint32_t *total_dev,
+                                int32_t *olead, int32_t *otrail, int32_t *ocount, uint8_t *ocode, int32_t *alead,
+                                int32_t *atrail, hipStream_t s);
+
 // exclusive scan of u32 (in place allowed), returns total in *total_dev
 size_t scan_temp_bytes(uint64_t n);
 hipError_t exclusive_scan_u32(const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *total_dev,

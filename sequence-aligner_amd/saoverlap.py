@@ -25,7 +25,10 @@ SA_IDS_AUTO, SA_IDS_STRICT, SA_IDS_WIDE = 0, 1, 2
 SA_OPT_KEEP_PAIRS, SA_OPT_TIMING, SA_OPT_ALIGN_KERNEL, SA_OPT_ALIGNER, SA_OPT_LOCAL_BATCH_MB = 1, 2, 3, 4, 5
 SA_OPT_SERIAL_SHARDS, SA_OPT_LAUNCH_SLICE, SA_OPT_FIRST_PASS = 6, 7, 8
 SA_OPT_PASS_BUDGET_MB, SA_OPT_LEAN_MEMORY = 9, 10   # sharded contexts: lead-range passes, scratch release
+SA_OPT_STRANDS = 11                              # both-strand overlaps (enum sa_strands)
 SA_ALIGNER_LINEAR, SA_ALIGNER_QUADRATIC = 0, 1   # --linear-align / --quadratic-align
+SA_STRANDS_FORWARD, SA_STRANDS_BOTH = 0, 1       # --forward-strand (default) / --both-strands
+STRANDS_FORWARD, STRANDS_BOTH = SA_STRANDS_FORWARD, SA_STRANDS_BOTH
 SA_STATS_PER_READ_REGIONS, SA_STATS_RECOUNTED = 1, 2    # sa_stats.flags bits of the last build
 ALIGN_AUTO, ALIGN_GROUP, ALIGN_LANE, ALIGN_LANE_SUMMARY = 0, 1, 2, 3
 STAGES = ("pack", "emit", "sort", "buckets", "pairs", "order", "align", "exchange",
@@ -34,6 +37,7 @@ ERRORS = {-1: "SA_E_ARG", -2: "SA_E_INPUT", -3: "SA_E_NON_ACGT", -4: "SA_E_ID_RA
           -6: "SA_E_DEGENERATE", -7: "SA_E_HIP", -8: "SA_E_NOMEM", -9: "SA_E_RCCL", -10: "SA_E_STATE",
           -11: "SA_E_OVERFLOW"}
 FLAG_DUD, FLAG_VALID, FLAG_OVL_VALID = 1, 2, 4
+FLAG_FLIP_TRAIL, FLAG_FLIP_LEAD = 8, 16   # both strands: aligned with the trail / the lead reverse-complemented
 
 # exported symbols declared in include/sa_overlap.h
 EXPORTS = ("sa_default_settings", "sa_ctx_create", "sa_ctx_destroy", "sa_last_error", "sa_load_hoxd",
@@ -43,7 +47,7 @@ EXPORTS = ("sa_default_settings", "sa_ctx_create", "sa_ctx_destroy", "sa_last_er
            "sa_sync", "sa_dist_init", "sa_dist_local_kmers", "sa_dist_emit", "sa_dist_count", "sa_dist_partials",
            "sa_dist_reduce", "sa_dist_codes", "sa_dist_set_reads", "sa_ctx_create_multi", "sa_rccl_unique_id",
            "sa_ctx_create_rank", "sa_exchanged_bytes", "sa_dist_buckets", "sa_dist_plan", "sa_dist_count_pass",
-           "sa_dist_reduce_pass", "sa_get_shard_info")
+           "sa_dist_reduce_pass", "sa_get_shard_info", "sa_get_dispatch_strands")
 RCCL_ID_BYTES = 128
 
 
@@ -122,6 +126,8 @@ def lib():
             L.sa_dist_count_pass.argtypes = [vp, C.c_uint32, C.c_uint32, P(C.c_uint64)]
             L.sa_dist_reduce_pass.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32]
             L.sa_get_shard_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint64), P(C.c_uint64)]
+        if hasattr(L, "sa_get_dispatch_strands"):
+            L.sa_get_dispatch_strands.argtypes = [vp, P(P(C.c_uint8)), P(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -174,7 +180,7 @@ class Overlapper:
     def __init__(self, device=0, timing=False, keep_pairs=False, align_kernel=ALIGN_AUTO,
                  aligner=SA_ALIGNER_LINEAR, local_batch_mb=None, gpus=1, shards=1, rank=None, nranks=None,
                  rccl_id=None, serial_shards=False, launch_slice=0, first_pass=0, pass_budget_mb=0,
-                 lean_memory=False, **kw):
+                 lean_memory=False, strands=SA_STRANDS_FORWARD, **kw):
         self.s = settings(**kw)
         h = C.c_void_p()
         if rank is not None:
@@ -207,6 +213,8 @@ class Overlapper:
             self._chk(lib().sa_set_option(h, SA_OPT_PASS_BUDGET_MB, pass_budget_mb))
         if lean_memory:
             self._chk(lib().sa_set_option(h, SA_OPT_LEAN_MEMORY, 1))
+        if strands != SA_STRANDS_FORWARD:
+            self._chk(lib().sa_set_option(h, SA_OPT_STRANDS, strands))
 
     def kmer_histogram(self):
         """(uniques, {bucket size: number of hashes}) -- KmerTable.uniqueKmers /
@@ -224,6 +232,12 @@ class Overlapper:
     def set_aligner(self, aligner):
         """SA_OPT_ALIGNER: SA_ALIGNER_LINEAR (--linear-align) or SA_ALIGNER_QUADRATIC."""
         self._chk(lib().sa_set_option(self.h, SA_OPT_ALIGNER, aligner))
+
+    def set_strands(self, strands):
+        """SA_OPT_STRANDS: STRANDS_FORWARD (default) or STRANDS_BOTH -- overlaps of reads
+        from either strand (adj:I records with signed hangs after the forward block;
+        include/sa_overlap.h).  Invalidates the candidates and alignments."""
+        self._chk(lib().sa_set_option(self.h, SA_OPT_STRANDS, strands))
 
     def close(self):
         if getattr(self, "h", None):
@@ -290,6 +304,15 @@ class Overlapper:
         n = C.c_size_t()
         self._chk(lib().sa_get_dispatch(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return _arr(a, n.value), _arr(b, n.value), _arr(c, n.value)
+
+    def dispatch_strands(self):
+        """One strand code per dispatch() entry: 0 forward pair, 1 trail flipped, 2 lead
+        flipped (all 0 unless strands=STRANDS_BOTH)."""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+        self._chk(lib().sa_get_dispatch_strands(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.uint8)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
 
     def pairs(self):
         a, b, c = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
