@@ -28,6 +28,13 @@ extern "C" {
 
 #define SA_ABI_VERSION 2
 
+/* Alignment errors (SA_E_NON_ACGT, SA_E_SHORT_READ, SA_E_DEGENERATE, SA_E_OVERFLOW)
+ * are per pair.  The reference stops at the first failing pair in dispatch order;
+ * the device aligns all pairs at once and keeps the code of the failing pair that
+ * reports first (one compare-and-swap on a device word), so when pairs of one run
+ * fail in different ways the call returns one of their codes, not necessarily the
+ * first in dispatch order.  A single pair that is both too short and holds a
+ * non-ACGT base gives SA_E_SHORT_READ, as the reference does. */
 enum sa_status {
     SA_OK = 0,
     SA_E_ARG = -1,         /* bad argument / flag (Project4.readArgs exit 1) */
@@ -137,6 +144,32 @@ int sa_kmer_histogram(sa_ctx *ctx, uint64_t *uniques, const uint64_t **size, con
  * (BioLibs.scala:267-368) under SA_OPT_ALIGNER = SA_ALIGNER_QUADRATIC. */
 int sa_align(sa_ctx *ctx);
 int sa_get_alignments(sa_ctx *ctx, const sa_alignment **out, size_t *n);
+
+/* Which kernels the last sa_align / sa_device_align on this context chose (the
+ * choice follows from the longest and shortest read, k, min_identity, the cost
+ * matrix divided by its common divisor with the gap costs, and the gap signs).
+ * Filled before anything is launched, so it also describes an alignment that
+ * then failed (SA_E_SHORT_READ, ...).  Reporting it launches nothing. */
+typedef struct sa_align_info {
+    int32_t aligner;    /* enum sa_aligner */
+    int32_t kernel;     /* 1 lane-group, 2 lane-per-pair with stored traceback codes,
+                           3 lane-per-pair with per-cell path summaries, 4 quadratic */
+    int32_t width;      /* lanes per pair G (kernel 1: 16 / 32 / 64) or band registers per
+                           lane LW (kernels 2, 3: 16 / 24 / 32); 0 for the quadratic aligner */
+    int32_t exact;      /* 1: every band is exactly 16 cells wide (unmasked lane kernels) */
+    int32_t p1_x2;      /* 1: phase 1 ran two pairs per lane in packed 16-bit halves */
+    int32_t p2_x2;      /* 1: phase 2 did too */
+    int32_t nseg;       /* phase-1 row segments: 0 the one-segment packed kernel, >= 1 the
+                           segmented one; -1 when p1_x2 is 0 */
+    int32_t cost_bits;  /* 8 or 16: the width of the kernels' cost packs */
+} sa_align_info;
+/* SA_E_STATE before the first alignment on the context; SA_E_ARG on a sharded
+ * context (its shards may choose differently).  With SA_STRANDS_BOTH the forward
+ * and the flipped block hold reads of the same lengths and take the same path:
+ * that one path is reported, with the forward block's nseg (the automatic segment
+ * count also follows a block's pair count); SA_E_STATE if the blocks ever differed
+ * in another field. */
+int sa_get_align_info(const sa_ctx *ctx, sa_align_info *out);
 
 /* calcOverlaps (Project4.scala:795-825): AMOS {OVL} records of valid overlaps in
  * dispatch order.  path == NULL writes to stdout; an existing file is replaced. */

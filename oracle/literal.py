@@ -335,7 +335,13 @@ def cost(s, a, b):  # the closure at :142-160 (MatchError on non-ACGT)
     return s.cost[_HX[a.upper()]][_HX[b.upper()]]
 
 
-def fast_dovetail(idA, A, idB, B, s):  # BioLibs.generateFastDovetailAlignmentSet :596-822 (one B)
+def fast_dovetail(idA, A, idB, B, s, diag=None):  # BioLibs.generateFastDovetailAlignmentSet :596-822 (one B)
+    # diag (a dict, optional) only records: per phase its maximum, the cells of the scan that
+    # hold it, and the backtrack steps where two or three of M / X / Y equal the running
+    # maximum (sa_oracle.h orc_diag_t); the alignment does not depend on it
+    if diag is None:
+        diag = {}
+    diag.update(p1_max=0, p1_cells=0, p1_tied=0, p2_max=0, p2_cells=0, p2_tied=0)
     gO, gE = s.gapOpen, s.gapExtend
     width = max(s.kmerSize, int(np.floor(F32(len(A)) * (F32(1) - s.minIdentity))) + 1)  # :619-620
     M = [[0] * (width + 1) for _ in range(len(A) + 1)]
@@ -354,11 +360,15 @@ def fast_dovetail(idA, A, idB, B, s):  # BioLibs.generateFastDovetailAlignmentSe
             t = max(M[i][j], max(X[i][j], Y[i][j]))
             if t > mx:
                 mx, maxLoc = t, (i, j)
+    diag["p1_max"] = mx
+    diag["p1_cells"] = sum(max(M[i][j], X[i][j], Y[i][j]) == mx for i in range(1, len(A) + 1)
+                           for j in range(1, width + 1)) if mx > 0 else 0
     i, j = maxLoc  # :673-689
     mx = max(M[i][j], X[i][j], Y[i][j])
     while True:
         if i < 0 or j < 0:
             raise IndexError("degenerate phase-1 backtrack")
+        diag["p1_tied"] += [M[i][j], X[i][j], Y[i][j]].count(mx) >= 2
         if M[i][j] == mx:
             i -= 1; j -= 1
         elif X[i][j] == mx:
@@ -392,6 +402,9 @@ def fast_dovetail(idA, A, idB, B, s):  # BioLibs.generateFastDovetailAlignmentSe
             t = max(M[u][k], max(X[u][k], Y[u][k]))
             if t > mx:
                 mx, maxLoc = t, (u, k)
+    diag["p2_max"] = mx
+    diag["p2_cells"] = sum(max(M[u][k], X[u][k], Y[u][k]) == mx for u in range(0, doveLength + 1)
+                           for k in range(0, width + 1)) if mx > 0 else 0
     opt = maxLoc  # :768-809
     u, k = maxLoc
     c = e = 0
@@ -399,6 +412,7 @@ def fast_dovetail(idA, A, idB, B, s):  # BioLibs.generateFastDovetailAlignmentSe
     while True:
         i = u + doveStart
         j = k - zeroRow + u
+        diag["p2_tied"] += [M[u][k], X[u][k], Y[u][k]].count(mx) >= 2
         if M[u][k] == mx:
             pa, pb = A[i - 1], B[j - 1]; u -= 1
         elif X[u][k] == mx:

@@ -32,6 +32,13 @@ class Align(C.Structure):
 ALIGN_FIELDS = [f[0] for f in Align._fields_]
 
 
+class Diag(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("p1_max", "p1_cells", "p1_tied", "p2_max", "p2_cells", "p2_tied")]
+
+
+DIAG_FIELDS = [f[0] for f in Diag._fields_]
+
+
 def build():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
@@ -70,7 +77,10 @@ def lib():
         L.orc_align_pair.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
                                      P(Settings), P(Align)]
         L.orc_align_pair_local.argtypes = L.orc_align_pair.argtypes
-        L.orc_trove_order.argtypes = [P(C.c_int32), C.c_size_t, P(C.c_int32), P(C.c_int32)]
+        L.orc_align_pair_diag.argtypes = L.orc_align_pair.argtypes + [P(Diag)]
+        L.orc_align_batch_diag.argtypes = [C.c_char_p, P(C.c_uint64), C.c_uint32, P(C.c_int32), P(C.c_int32),
+                                           C.c_size_t, P(Settings), P(Align), P(Diag)]
+        L.orc_trove_order.argtypes =[P(C.c_int32), C.c_size_t, P(C.c_int32), P(C.c_int32)]
         L.orc_align_batch.argtypes = [C.c_char_p, P(C.c_uint64), C.c_uint32, P(C.c_int32), P(C.c_int32), C.c_size_t,
                                       P(Settings), C.c_int, P(Align)]
         L.orc_max_threads.restype = C.c_int
@@ -194,6 +204,40 @@ def align_pair(A, B, id_a=1, id_b=2, settings=None, quadratic=False):
     if rc:
         raise OracleError(rc)
     return {n: getattr(out, n) for n in ALIGN_FIELDS}
+
+
+def align_pair_diag(A, B, id_a=1, id_b=2, settings=None):
+    """align_pair (dovetail aligner) plus the pair's tie diagnostics (orc_align_pair_diag):
+    (alignment dict, {p1_max, p1_cells, p1_tied, p2_max, p2_cells, p2_tied})."""
+    s = settings or default_settings()
+    out, dg = Align(), Diag()
+    rc = lib().orc_align_pair_diag(A.encode(), len(A), B.encode(), len(B), id_a, id_b, C.byref(s), C.byref(out),
+                                   C.byref(dg))
+    if rc:
+        raise OracleError(rc)
+    return {n: getattr(out, n) for n in ALIGN_FIELDS}, {n: getattr(dg, n) for n in DIAG_FIELDS}
+
+
+def align_batch_diag(reads, lead, trail, settings=None):
+    """The dovetail alignments and tie diagnostics of the given pairs of `reads` (ids
+    1-based): (int32[n, len(ALIGN_FIELDS)], int32[n, len(DIAG_FIELDS)])."""
+    s = settings or default_settings()
+    bases = b"".join(r.encode() if isinstance(r, str) else bytes(r) for r in reads)
+    off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in reads])
+    ld = np.ascontiguousarray(lead, dtype=np.int32)
+    tr = np.ascontiguousarray(trail, dtype=np.int32)
+    n = len(ld)
+    out, dg = (Align * max(n, 1))(), (Diag * max(n, 1))()
+    P = C.POINTER
+    rc = lib().orc_align_batch_diag(bases, off.ctypes.data_as(P(C.c_uint64)), len(reads),
+                                    ld.ctypes.data_as(P(C.c_int32)), tr.ctypes.data_as(P(C.c_int32)), n,
+                                    C.byref(s), out, dg)
+    if rc:
+        raise OracleError(rc)
+    a = np.ctypeslib.as_array(C.cast(out, P(C.c_int32)), shape=(max(n, 1) * len(ALIGN_FIELDS),))
+    d = np.ctypeslib.as_array(C.cast(dg, P(C.c_int32)), shape=(max(n, 1) * len(DIAG_FIELDS),))
+    return a.reshape(-1, len(ALIGN_FIELDS))[:n].copy(), d.reshape(-1, len(DIAG_FIELDS))[:n].copy()
 
 
 def align_batch(bases, offsets, lead, trail, settings=None, threads=1):

@@ -361,8 +361,10 @@ typedef struct { int32_t *M, *X, *Y; size_t cap; } dp_buf;
 static void judge(orc_align_t *o, const orc_settings *s);
 
 static int align_one(dp_buf *b, const char *A, int32_t la, const char *B, int32_t lb,
-                     int32_t ida, int32_t idb, const orc_settings *s, orc_align_t *o) {
+                     int32_t ida, int32_t idb, const orc_settings *s, orc_align_t *o, orc_diag_t *dg) {
     const int32_t gO = s->gap_open, gE = s->gap_extend;
+    int32_t ncell = 0, ntied = 0; /* diagnostics only (orc_align_pair_diag): nothing below reads them */
+    if (dg) memset(dg, 0, sizeof(*dg));
     /* :619-620 width = max(k, floor(|A| * (1 - minId)).toInt + 1), Float product */
     float prod = (float)la * (1.0f - s->min_identity);
     int32_t fl = (int32_t)floor((double)prod);
@@ -407,15 +409,19 @@ static int align_one(dp_buf *b, const char *A, int32_t la, const char *B, int32_
             int32_t t = AT(M, i, j);
             if (AT(X, i, j) > t) t = AT(X, i, j);
             if (AT(Y, i, j) > t) t = AT(Y, i, j);
-            if (t > mx) { mx = t; mi = i; mj = j; }
+            if (t > mx) { mx = t; mi = i; mj = j; ncell = 1; }
+            else if (t == mx && mx > 0) ncell++;
         }
     }
+    if (dg) { dg->p1_max = mx; dg->p1_cells = ncell; }
     /* phase-1 greedy backtrack :673-689 */
     int32_t i = mi, j = mj;
 #define CMAX(i_, j_) (AT(M, i_, j_) > AT(X, i_, j_) ? (AT(M, i_, j_) > AT(Y, i_, j_) ? AT(M, i_, j_) : AT(Y, i_, j_)) \
                                                     : (AT(X, i_, j_) > AT(Y, i_, j_) ? AT(X, i_, j_) : AT(Y, i_, j_)))
     mx = CMAX(i, j);
     do {
+        ntied += (AT(M, i, j) == mx) + (AT(X, i, j) == mx) + (AT(Y, i, j) == mx) >= 2;
+        if (dg) dg->p1_tied = ntied;
         if (AT(M, i, j) == mx) { i--; j--; }
         else if (AT(X, i, j) == mx) { j--; }
         else if (AT(Y, i, j) == mx) { i--; }
@@ -431,7 +437,7 @@ static int align_one(dp_buf *b, const char *A, int32_t la, const char *B, int32_
         return ORC_OK;
     }
     const int32_t doveStart = i, doveLength = la - doveStart, zeroRow = width / 2;
-    mx = 0; mi = 0; mj = 0;
+    mx = 0; mi = 0; mj = 0; ncell = 0; ntied = 0;
     for (int32_t u = 0; u <= doveLength; u++) { /* :725-764 */
         for (int32_t k = 0; k <= width; k++) {
             int32_t ii = u + doveStart, jj = k - zeroRow + u;
@@ -461,9 +467,11 @@ static int align_one(dp_buf *b, const char *A, int32_t la, const char *B, int32_
                 } else AT(Y, u, k) = 0;
             }
             int32_t t = CMAX(u, k);
-            if (t > mx) { mx = t; mi = u; mj = k; }
+            if (t > mx) { mx = t; mi = u; mj = k; ncell = 1; }
+            else if (t == mx && mx > 0) ncell++;
         }
     }
+    if (dg) { dg->p2_max = mx; dg->p2_cells = ncell; }
     /* phase-2 greedy backtrack :768-809 */
     int32_t u = mi, k = mj, c = 0, e = 0;
     mx = CMAX(u, k);
@@ -471,6 +479,8 @@ static int align_one(dp_buf *b, const char *A, int32_t la, const char *B, int32_
         int32_t ii = u + doveStart, jj = k - zeroRow + u;
         char pa = ' ', pb = ' ';
         if (ii - 1 < 0 || ii - 1 >= la) return ORC_E_INDEX;
+        ntied += (AT(M, u, k) == mx) + (AT(X, u, k) == mx) + (AT(Y, u, k) == mx) >= 2;
+        if (dg) dg->p2_tied = ntied;
         if (AT(M, u, k) == mx) {
             if (jj - 1 < 0 || jj - 1 >= lb) return ORC_E_INDEX;
             pa = A[ii - 1]; pb = B[jj - 1]; u--;
@@ -603,9 +613,34 @@ static void judge(orc_align_t *o, const orc_settings *s) {
 int orc_align_pair(const char *A, int32_t la, const char *B, int32_t lb, int32_t ida, int32_t idb,
                    const orc_settings *s, orc_align_t *out) {
     dp_buf b = {0};
-    int rc = align_one(&b, A, la, B, lb, ida, idb, s, out);
+    int rc = align_one(&b, A, la, B, lb, ida, idb, s, out, NULL);
     free(b.M); free(b.X); free(b.Y);
     if (rc == ORC_OK) judge(out, s);
+    return rc;
+}
+
+int orc_align_pair_diag(const char *A, int32_t la, const char *B, int32_t lb, int32_t ida, int32_t idb,
+                        const orc_settings *s, orc_align_t *out, orc_diag_t *diag) {
+    dp_buf b = {0};
+    int rc = align_one(&b, A, la, B, lb, ida, idb, s, out, diag);
+    free(b.M); free(b.X); free(b.Y);
+    if (rc == ORC_OK) judge(out, s);
+    return rc;
+}
+
+int orc_align_batch_diag(const char *bases, const uint64_t *offsets, uint32_t n_reads, const int32_t *lead,
+                         const int32_t *trail, size_t n_pairs, const orc_settings *s, orc_align_t *out,
+                         orc_diag_t *diag) {
+    dp_buf b = {0};
+    int rc = ORC_OK;
+    for (size_t p = 0; p < n_pairs && rc == ORC_OK; p++) {
+        const int32_t a = lead[p] - 1, t = trail[p] - 1;
+        if (a < 0 || t < 0 || (uint32_t)a >= n_reads || (uint32_t)t >= n_reads) { rc = ORC_E_INPUT; break; }
+        rc = align_one(&b, bases + offsets[a], (int32_t)(offsets[a + 1] - offsets[a]), bases + offsets[t],
+                       (int32_t)(offsets[t + 1] - offsets[t]), lead[p], trail[p], s, &out[p], &diag[p]);
+        if (rc == ORC_OK) judge(&out[p], s);
+    }
+    free(b.M); free(b.X); free(b.Y);
     return rc;
 }
 
@@ -642,7 +677,7 @@ int orc_align_batch(const char *bases, const uint64_t *offsets, uint32_t n_reads
             int rc = ORC_E_INPUT;
             if (a < n_reads && t < n_reads) {
                 rc = align_one(&b, bases + offsets[a], (int32_t)(offsets[a + 1] - offsets[a]), bases + offsets[t],
-                               (int32_t)(offsets[t + 1] - offsets[t]), lead[i], trail[i], s, &out[i]);
+                               (int32_t)(offsets[t + 1] - offsets[t]), lead[i], trail[i], s, &out[i], NULL);
                 if (rc == ORC_OK) judge(&out[i], s);
             }
             if (rc != ORC_OK) {
@@ -886,7 +921,8 @@ out_kd:
         int32_t la = (int32_t)(c->off[a] - c->off[a - 1]);
         int32_t lb = (int32_t)(c->off[b] - c->off[b - 1]);
         orc_align_t *o = &c->aligns[q];
-        if ((rc = (quadratic ? align_local : align_one)(&db, A, la, B, lb, a, b, s, o))) break;
+        if ((rc = quadratic ? align_local(&db, A, la, B, lb, a, b, s, o)
+                            : align_one(&db, A, la, B, lb, a, b, s, o, NULL))) break;
         judge(o, s);
         if (o->valid && o->ovl_valid) {
             char rec[160];

@@ -130,6 +130,26 @@ size_t orc_ovl(const orc_ctx *c, const char **text);
 int orc_align_pair(const char *A, int32_t len_a, const char *B, int32_t len_b,
                    int32_t id_a, int32_t id_b, const orc_settings *s, orc_align_t *out);
 
+/* orc_align_pair plus how tie-prone the pair is (test fixtures are judged by
+ * it; `out` is exactly orc_align_pair's).  A phase's maximum is the value its
+ * argmax scan ends with (`t > mx`, first cell in row-major order wins); cells =
+ * how many cells of the scan hold that value (0 when the maximum is 0); tied =
+ * how many steps of the phase's greedy backtrack stood on a cell where two or
+ * three of M / X / Y equal the running maximum (the walk then prefers M over X
+ * over Y).  Phase-2 fields are 0 for a dud.  On an error the fields of the
+ * phases completed so far are set. */
+typedef struct {
+    int32_t p1_max, p1_cells, p1_tied;
+    int32_t p2_max, p2_cells, p2_tied;
+} orc_diag_t;
+int orc_align_pair_diag(const char *A, int32_t len_a, const char *B, int32_t len_b,
+                        int32_t id_a, int32_t id_b, const orc_settings *s, orc_align_t *out, orc_diag_t *diag);
+/* the same over a dispatch list (ids 1-based, as orc_align_batch), one diag per
+ * pair, on one thread; stops at and returns the first error */
+int orc_align_batch_diag(const char *bases, const uint64_t *offsets, uint32_t n_reads, const int32_t *lead,
+                         const int32_t *trail, size_t n_pairs, const orc_settings *s, orc_align_t *out,
+                         orc_diag_t *diag);
+
 /* The dovetail aligner over a dispatch list on `threads` OpenMP threads (0 =
  * all): the aligner leg of the CPU baseline (genBlockMTAlign's actor pool,
  * Project4.scala:725-790; pairs are independent). */

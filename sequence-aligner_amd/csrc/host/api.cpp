@@ -1540,6 +1540,15 @@ int device_align(sa_ctx *c, bool readback) {
     const bool use_lane = c->align_kernel >= 2 || (c->align_kernel == 0 && lane_fits);
     const int32_t wmin = std::max(c->set.kmer_size, (int32_t)floor((double)((float)minL * omm)) + 1);
     const bool exact = wmin == 15 && wmax == 15 && lw == 16;  // every band exactly 16 cells wide
+    // the path taken below (sa_get_align_info): recorded before anything is launched
+    c->ainfo = sa_align_info{};
+    c->ainfo.aligner = c->aligner;
+    c->ainfo.kernel = c->aligner == SA_ALIGNER_QUADRATIC ? 4 : (!use_lane ? 1 : (c->align_kernel == 3 ? 3 : 2));
+    c->ainfo.width = c->aligner == SA_ALIGNER_QUADRATIC ? 0 : (use_lane ? lw : G);
+    c->ainfo.exact = c->aligner == SA_ALIGNER_LINEAR && use_lane && exact;
+    c->ainfo.nseg = -1;
+    c->ainfo.cost_bits = cost_bits;
+    c->ainfo_set = true;
     AlignParams P;
     P.k = c->set.kmer_size;
     P.gap_open = gap_open;
@@ -1594,9 +1603,12 @@ int device_align(sa_ctx *c, bool readback) {
                 // row segments when the waves are few enough for the last round to matter: units of
                 // 1 / nseg of a wave, ~20+ per SIMD (1,024 SIMDs), at most 8, rows >= 32 per segment
                 const uint32_t ng = dovetail_p1x2_groups(nd);
-                int32_t nseg = (int32_t)std::min<uint64_t>(8, (20 * 1024 + ng - 1) / ng);
+                int32_t nseg = (int32_t)std::min<uint64_t>(8, (20 * 1024 + ng - 1) / std::max(ng, 1u));
                 nseg = std::max(1, std::min(nseg, (int32_t)(maxL / 32)));
                 if (const char *e = getenv("SA_P1_SEGS")) nseg = atoi(e);  // A/B: 0 = one-segment kernel
+                c->ainfo.p1_x2 = 1;
+                c->ainfo.p2_x2 = c->align_kernel != 3 && maxL < 4096;  // (x2tb below)
+                c->ainfo.nseg = std::max(nseg, 0);
                 if (nseg >= 1) {
                     uint32_t *tf, *st = nullptr;
                     ENSURE(c->d_p1tf, (uint64_t)ng + 1, &tf);
@@ -2352,6 +2364,21 @@ int sa_set_option(sa_ctx *c, int option, int64_t value) {
     default: return fail(c, SA_E_ARG, "unknown option");
     }
     return c->multi ? multi_set_option(c, option, value) : SA_OK;
+}
+
+int sa_get_align_info(const sa_ctx *c, sa_align_info *out) {
+    if (!c || !out || c->multi) return SA_E_ARG;
+    if (!c->ainfo_set) return SA_E_STATE;
+    if (c->strands == SA_STRANDS_BOTH && c->aug && c->aug->ainfo_set) {
+        // the flipped block: reads of the same lengths, so the same path (nseg aside:
+        // the automatic segment count also follows the block's pair count)
+        const sa_align_info &f = c->ainfo, &r = c->aug->ainfo;
+        if (f.aligner != r.aligner || f.kernel != r.kernel || f.width != r.width || f.exact != r.exact ||
+            f.p1_x2 != r.p1_x2 || f.p2_x2 != r.p2_x2 || f.cost_bits != r.cost_bits)
+            return SA_E_STATE;
+    }
+    *out = c->ainfo;
+    return SA_OK;
 }
 
 int sa_get_stats(const sa_ctx *c, sa_stats *out) {

@@ -164,6 +164,8 @@ struct sa_ctx {
     int aligner = SA_ALIGNER_LINEAR;  // SA_OPT_ALIGNER (--linear-align / --quadratic-align)
     uint64_t local_batch_bytes = 16ull << 30;  // traceback-code budget of one quadratic launch
     bool built = false, aligned = false;
+    sa_align_info ainfo{};      // the kernels the last device_align chose (sa_get_align_info)
+    bool ainfo_set = false;
     // both strands (SA_OPT_STRANDS = SA_STRANDS_BOTH): the augmented set, reads 1..2N with
     // read N + i = rc(read i), lives in a child context `aug` (wide ids; host metadata
     // from the lengths alone, its ASCII buffer this context's, second half filled by

@@ -47,7 +47,7 @@ EXPORTS = ("sa_default_settings", "sa_ctx_create", "sa_ctx_destroy", "sa_last_er
            "sa_sync", "sa_dist_init", "sa_dist_local_kmers", "sa_dist_emit", "sa_dist_count", "sa_dist_partials",
            "sa_dist_reduce", "sa_dist_codes", "sa_dist_set_reads", "sa_ctx_create_multi", "sa_rccl_unique_id",
            "sa_ctx_create_rank", "sa_exchanged_bytes", "sa_dist_buckets", "sa_dist_plan", "sa_dist_count_pass",
-           "sa_dist_reduce_pass", "sa_get_shard_info", "sa_get_dispatch_strands")
+           "sa_dist_reduce_pass", "sa_get_shard_info", "sa_get_dispatch_strands", "sa_get_align_info")
 RCCL_ID_BYTES = 128
 
 
@@ -62,6 +62,11 @@ class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("kmers", "buckets", "role_pairs", "pairs", "dispatched", "aligned",
                                            "ovl_records", "dp_cells")] + [("id_mode", C.c_int32),
                                                                           ("flags", C.c_int32)]
+
+
+class AlignInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("aligner", "kernel", "width", "exact", "p1_x2", "p2_x2", "nseg",
+                                         "cost_bits")]
 
 
 ALIGN_FIELDS = ("lead", "trail", "start_i", "start_j", "end_i", "end_j", "correct", "error", "ahg", "bhg",
@@ -128,6 +133,8 @@ def lib():
             L.sa_get_shard_info.argtypes = [vp, P(C.c_uint32), P(C.c_uint64), P(C.c_uint64)]
         if hasattr(L, "sa_get_dispatch_strands"):
             L.sa_get_dispatch_strands.argtypes = [vp, P(P(C.c_uint8)), P(C.c_size_t)]
+        if hasattr(L, "sa_get_align_info"):
+            L.sa_get_align_info.argtypes = [vp, P(AlignInfo)]
         _lib = L
     return _lib
 
@@ -327,6 +334,15 @@ class Overlapper:
             return np.zeros((0, len(ALIGN_FIELDS)), dtype=np.int32)
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=(n.value * len(ALIGN_FIELDS),))
         return raw.reshape(n.value, len(ALIGN_FIELDS)).copy()
+
+    def align_info(self):
+        """The kernels the last align() / device_align() chose (sa_get_align_info), also
+        after one that failed: {aligner, kernel (1 lane-group, 2 lane-per-pair, 3
+        lane-per-pair with path summaries, 4 quadratic), width (G or LW), exact, p1_x2,
+        p2_x2, nseg (-1 unless p1_x2), cost_bits}."""
+        ai = AlignInfo()
+        self._chk(lib().sa_get_align_info(self.h, C.byref(ai)))
+        return {f[0]: getattr(ai, f[0]) for f in AlignInfo._fields_}
 
     def ovl(self):
         t, n = C.c_char_p(), C.c_size_t()

@@ -37,6 +37,11 @@ def check(oracle_mod, reads, cost, quadratic, **st):
     assert len(al) == len(r.lead) > 100
     for name in ALIGN_CMP:
         np.testing.assert_array_equal(al[:, sao.ALIGN_FIELDS.index(name)], r.align_field(name), err_msg=name)
+    flags = al[:, sao.ALIGN_FIELDS.index("flags")]
+    np.testing.assert_array_equal((flags & sao.FLAG_DUD) != 0, r.align_field("is_dud") != 0)
+    np.testing.assert_array_equal((flags & sao.FLAG_VALID) != 0, r.align_field("valid") != 0)
+    np.testing.assert_array_equal((flags & sao.FLAG_OVL_VALID) != 0,
+                                  (r.align_field("ovl_valid") != 0) & (r.align_field("valid") != 0))
     assert ov.ovl() == r.ovl
     return ov
 
@@ -107,20 +112,49 @@ def test_costs_beyond_int16_fail_exactly():
     assert e.value.name == "SA_E_OVERFLOW"
 
 
-@pytest.mark.parametrize("cost", ["hoxd70", "near_16bit"])
-def test_two_pairs_per_lane_kernels(oracle_mod, cost):
-    """Reads of 467..500 bp (every band exactly 16 cells) with int8 costs: both
-    phases run two pairs per lane in packed 16-bit halves, pairs
-    of different trail lengths side by side.  'near_16bit' puts the largest
-    score (127 x 500 + bias) within 2,000 of the 16-bit limit."""
+def assert_packed_or_masked(ov, k, nseg):
+    """k = 15: every band of these reads is exactly 15, so both phases run two pairs per lane
+    (nseg: the phase-1 segment count, None = the automatic choice).  k = 12: the bands are 12,
+    which is the plain LW = 16 masked kernel pair, one pair per lane."""
+    info = ov.align_info()
+    if k == 15:
+        assert (info["exact"], info["p1_x2"], info["p2_x2"]) == (1, 1, 1), info
+        assert nseg is None or info["nseg"] == nseg, info
+    else:
+        assert (info["kernel"], info["width"], info["exact"], info["p1_x2"]) == (2, 16, 0, 0), info
+
+
+def two_pair_reads():
+    rng = np.random.default_rng(21)
+    reads = H.mutate(H.synth_reads(200, 490, 4000, gc=0.45, seed=21, mixed=(470, 497)), rng, 3)
+    assert 467 <= min(map(len, reads)) and max(map(len, reads)) <= 500
+    return reads
+
+
+def segment_reads():
+    rng = np.random.default_rng(22)
+    return H.mutate(H.synth_reads(240, 490, 4000, gc=0.45, seed=22, mixed=(467, 500)), rng, 3)
+
+
+def near_16bit(cost):
     c = list(HOXD70)
     if cost == "near_16bit":
         c[0] = c[15] = 127
         c[5] = c[10] = 113
-    rng = np.random.default_rng(21)
-    reads = H.mutate(H.synth_reads(200, 490, 4000, gc=0.45, seed=21, mixed=(470, 497)), rng, 3)
-    assert 467 <= min(map(len, reads)) and max(map(len, reads)) <= 500
-    check(oracle_mod, reads, c, False, kmer_size=12)
+    return c
+
+
+@pytest.mark.parametrize("cost", ["hoxd70", "near_16bit"])
+def test_two_pairs_per_lane_kernels(oracle_mod, monkeypatch, cost):
+    """Reads of 467..500 bp at kmer_size=15 (every band exactly 15, i.e. 16 cells) with int8
+    costs: both phases run two pairs per lane in packed 16-bit halves, pairs
+    of different trail lengths side by side, and sa_get_align_info says so.  'near_16bit' puts
+    the largest score (127 x 500 + bias) within 2,000 of the 16-bit limit.  (Until it asserted
+    the path this test passed kmer_size=12: bands of 12, the LW = 16 masked kernels -- now the
+    k = 12 test below.)"""
+    monkeypatch.delenv("SA_P1_SEGS", raising=False)
+    ov = check(oracle_mod, two_pair_reads(), near_16bit(cost), False, kmer_size=15)
+    assert_packed_or_masked(ov, 15, None)
 
 
 @pytest.mark.parametrize("segs", ["0", "1", "2", "5", "8"])
@@ -128,8 +162,21 @@ def test_phase1_row_segments(oracle_mod, monkeypatch, segs):
     """Phase 1 of the two-pairs-per-lane aligner in row segments (dovetail_p1x2_seg_kernel,
     DESIGN.md 4.6): the lanes' state handed between ticketed one-wave workgroups through
     device-scope atomics.  Every segment count -- 0 is the one-segment kernel -- gives the
-    oracle's alignments, on reads of 467..500 bp (pairs of different lengths in one wave)."""
+    oracle's alignments, on reads of 464..503 bp at kmer_size=15 (pairs of different lengths
+    in one wave), and sa_get_align_info reports that count."""
     monkeypatch.setenv("SA_P1_SEGS", segs)
-    rng = np.random.default_rng(22)
-    reads = H.mutate(H.synth_reads(240, 490, 4000, gc=0.45, seed=22, mixed=(467, 500)), rng, 3)
-    check(oracle_mod, reads, HOXD70, False, kmer_size=12)
+    ov = check(oracle_mod, segment_reads(), HOXD70, False, kmer_size=15)
+    assert_packed_or_masked(ov, 15, int(segs))
+
+
+@pytest.mark.parametrize("case", ["hoxd70", "near_16bit", "segs2"])
+def test_same_reads_at_k12_run_the_masked_kernels(oracle_mod, monkeypatch, case):
+    """The reads of the two tests above at kmer_size=12: bands of 12, so exact == 0 and the
+    plain LW = 16 masked kernels run, one pair per lane; SA_P1_SEGS is not read."""
+    if case == "segs2":
+        monkeypatch.setenv("SA_P1_SEGS", "2")
+        ov = check(oracle_mod, segment_reads(), HOXD70, False, kmer_size=12)
+    else:
+        monkeypatch.delenv("SA_P1_SEGS", raising=False)
+        ov = check(oracle_mod, two_pair_reads(), near_16bit(case), False, kmer_size=12)
+    assert_packed_or_masked(ov, 12, None)
